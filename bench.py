@@ -335,6 +335,52 @@ def host_cost_probe(limit_s: float = 120.0) -> dict:
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20 - 64 * 1024   # (64 MB in all, .npy headers included)
+
+
+def last_step_outputs(last, opac, scales, shs) -> dict:
+    """What a caller of the timed path receives from one step, as host arrays: the rasterizer's outputs in the stacked
+    layout -- color (3,F,H,W), radii (F,N), allmap (8,F,H,W) -- and the gradients of its inputs."""
+    import numpy as np
+    if "stacked" in last:
+        color, radii, allmap, gm, gr, g2d = last["stacked"]
+    else:   # (one call per frame: the frames stacked as the stacked call returns them)
+        fr = last["frames"]
+        color, allmap = (torch.stack([f[i] for f in fr], 1) for i in (0, 2))
+        radii, gm, gr, g2d = (torch.stack([f[i] for f in fr], 0) for i in (1, 3, 4, 5))
+    named = {"color": color, "radii": radii, "allmap": allmap, "dL_dmeans3D": gm, "dL_drotations": gr,
+             "dL_dmeans2D": g2d, "dL_dopacity": opac.grad, "dL_dscales": scales.grad, "dL_dsh": shs.grad}
+    out = {}
+    for k, t in named.items():
+        if t is None:
+            continue
+        a = t.detach().cpu().numpy()
+        out[k] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+    return out
+
+
+def dump_outputs(out_dir: str, arrays: dict, budget: int = DUMP_BUDGET_BYTES) -> dict:
+    """Writes arrays as out_dir/<name>.npy.  When they exceed the budget together, every array is replaced by a fixed
+    sample of its flattened elements (the same for the same name and shape on every run: seeded by the name, indices in
+    ascending order), each array keeping its share of the budget."""
+    import zlib
+
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    info = {}
+    for name, a in arrays.items():
+        entry = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        if total > budget:
+            k = max(1, a.nbytes * budget // total // a.itemsize)
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, k, replace=False))
+            a = a.reshape(-1)[idx]
+            entry["sampled_elements"] = int(k)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        info[name] = entry
+    return {"dir": out_dir, "arrays": info, "bytes": sum(os.path.getsize(os.path.join(out_dir, n + ".npy")) for n in info)}
+
+
 def replicas_main(args, world, rank, local_rank):
     """BASELINE.json configs[3]: `world` independent sequences, one process per GPU, nothing exchanged -- an RCCL
     barrier before the timed loop and one after it (the pattern of lab4d/utils/gpu_utils.py:6-128 /
@@ -412,6 +458,9 @@ def main():
     ap.add_argument("--replicas", type=int, default=0,
                     help="BASELINE.json configs[3]: N independent Stage-3 sequences, one per GPU, RCCL barrier at start "
                          "and end only; prints the aggregate images/s of the full fitting step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step (image, radii, auxiliary planes, "
+                         "gradients) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (see dump_outputs)")
     ap.add_argument("--_torch_cpu_child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--_threads", type=int, default=8, help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -431,6 +480,8 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (the product has no CPU path)")
+    if args.replicas and args.dump_outputs:
+        raise SystemExit("--dump-outputs is not supported with --replicas")
     if args.replicas and (args.replicas == 1 or "WORLD_SIZE" in os.environ):
         return replicas_main(args, world, rank, local_rank)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -511,7 +562,9 @@ def main():
     # The frames of a step are independent until their gradients are summed: like Stage3Trainer, each one
     # is queued on its own HIP stream, so the tail of one frame's blend kernels overlaps the next frame's
     # projection / binning instead of leaving CUs idle (--frame-streams 0: one stream).
-    mode = {"streams": bool(args.frame_streams), "stacked": bool(args.stacked)}
+    mode = {"streams": bool(args.frame_streams), "stacked": bool(args.stacked), "capture": bool(args.dump_outputs)}
+    # --dump-outputs: the outputs of the latest step (references only; copied to the host after the timed region)
+    last = {}
     side = [torch.cuda.Stream(device=dev) for _ in range(FRAMES_PER_STEP)]
 
     def one_frame(i):
@@ -520,6 +573,8 @@ def main():
         m2d = torch.zeros_like(m, requires_grad=True)
         color, radii, allmap = rast(means3D=m, means2D=m2d, opacities=opac_f, shs=shs_f, scales=scales_f, rotations=r)
         torch.autograd.backward([color, allmap], [dc, do])
+        if mode["capture"]:
+            last.setdefault("frames", []).append((color.detach(), radii, allmap.detach(), m.grad, r.grad, m2d.grad))
         return m.grad, r.grad
 
     from vidu4d_amd import _C as native
@@ -593,9 +648,12 @@ def main():
         m2d = screen_dummy[0].detach().requires_grad_(True)
         color, radii, allmap = dsr.rasterize_frames(m, m2d, shs_f, opac_f, scales_f, r, rs_frames)
         torch.autograd.backward([color, allmap], [dc_st, do_st])
+        if mode["capture"]:
+            last["stacked"] = (color.detach(), radii, allmap.detach(), m.grad, r.grad, m2d.grad)
         return m.grad, r.grad
 
     def step_once():
+        last.clear()
         if use_dist:
             flat_view = claim_flat()
         else:
@@ -684,6 +742,12 @@ def main():
     enqueued = time.perf_counter() - t0   # (host side: all launches of the region queued; the GPU is still working)
     sync()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if mode["capture"]:
+        mode["capture"] = False
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, last_step_outputs(last, opac, scales, shs))
+        last.clear()
     rep_rates = []
     for _ in range(max(0, args.repeats)):
         sync()
@@ -789,6 +853,8 @@ def main():
     }
     if rccl_check is not None:
         out["rccl"] = rccl_check
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if world > 1 or use_dist:
         out["config"]["exchange"] = ("all-reduce of the step's flat gradient buffer joined before its buffer is reused, two steps "
                                      "later (the op-level loop has no optimizer between steps)" if args.exchange == "overlapped"

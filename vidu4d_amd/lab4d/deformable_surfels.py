@@ -96,7 +96,7 @@ class _WarpNetEval(nn.Module):
             se3 = qt.dual_quaternion_mul(t_art, qt.dual_quaternion_inverse(rest_art))
             A, c0 = sm.bone_affine((rest_art[0][:1], rest_art[1][:1]))
         if cq is None:
-            cq, ct = self.camera_mlp.get_vals(frame_id)
+            cq, ct = self.camera_mlp.get_vals(frame_id, fused=self.fused_stacks)
             bias = sm.frame_bias(None, None, 1, frame_id.device) if sm.has_delta else None
         else:
             main.wait_stream(s_cam)
@@ -298,8 +298,10 @@ class DeformableSurfels(GaussianModel):
         key = (int(frame_id.shape[0]), tuple(p.requires_grad for p in self._warp_param_list()))
         g = self.__dict__.get("_net_graph")
         if g is None or g[0] != key:
-            mod = _WarpNetEval(self.warp, self.camera_mlp, bool(self.opts.get("fused_bone_tables", True)),
-                               bool(self.opts.get("parallel_network_branches", True)),
+            # (one stream: captured on their own, the three branches would fork from a capture stream with no node on it
+            # yet and the graphs would start from several root nodes on three streams -- graphs whose replay crashed the
+            # HIP runtime on the host; the launches and their values are the same, only their order across branches differs)
+            mod = _WarpNetEval(self.warp, self.camera_mlp, bool(self.opts.get("fused_bone_tables", True)), False,
                                bool(self.opts.get("fused_dense_stacks", True)))
             try:
                 if self.opts.get("graphed_warp_networks", True) == "torch":   # (A/B: gradients through AccumulateGrad copies)
