@@ -1566,12 +1566,15 @@ __device__ __forceinline__ float row_reduce_scatter2(float a, float b, int lane)
 // MODE: BLEND_LITE reads only dL/dcolour and dL/d(alpha plane), BLEND_GEOM those and the planes 0, 2-4 (the caller promised
 // zeros elsewhere, aux_planes); the forward that filled the state may itself have run in that mode (no distortion moments,
 // no median contributor: never read here).
-// Register budget of the full instances: 80 VGPRs = 6 waves per SIMD (the allocator takes 88 = 5 waves when left alone;
-// no spills at 80, 10-13 spilled registers at 72).  Round 3, stacked launch at the headline size: 509 -> 497 us; 4 waves
-// per SIMD measure the same as 5 -- the kernel is bound by VALU issue, not by latency, the sixth wave only fills bubbles.
-// The LITE instances need 64-66 registers and are left to the allocator (7 waves, the LDS limit).
+// Register budget of the full and geometry instances: 72 VGPRs = 7 waves per SIMD (7 workgroups of 21.2 KB LDS per CU).
+// Round 3, stacked launch at the headline size: 5 -> 6 waves 509 -> 497 us; 4 waves per SIMD measure the same as 5 -- the
+// kernel is bound by VALU issue, not by latency, the extra waves only fill bubbles.  Since the eight "behind" recurrences
+// became one (BwdPixel::u), the loop needs 80 VGPRs without spills and 72 with 4 (FULL; GEOM none) spilled outside the
+// inner loop; headline step, stacked FULL instance: 352 us at 6 waves, 349 us at 7, and the bench value +1 % at 7
+// (NOTEBOOK, "After round 6").  -DSURFEL_BWD_WAVES_PER_EU=6 builds the 80-register variant.
+// The LITE instances need 66 registers and are left to the allocator (7 waves, the LDS limit).
 #ifndef SURFEL_BWD_WAVES_PER_EU
-#define SURFEL_BWD_WAVES_PER_EU 6
+#define SURFEL_BWD_WAVES_PER_EU 7
 #endif
 template <bool SPLIT, int MODE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == BLEND_LITE ? 1 : SURFEL_BWD_WAVES_PER_EU, MODE == BLEND_LITE ? 8 : SURFEL_BWD_WAVES_PER_EU)))
@@ -1711,12 +1714,8 @@ void blend_bwd_kernel(int W, int H, int grid_x, int grid_y, const Header* hdr,
             }
             const float inv = 1.0f / T_end;
             const float behind = T_end - s.T_final;  // sum of their blend weights
-            for (int ch = 0; ch < 3; ch++) s.accum_rec[ch] = sufC[ch] * inv;
-            s.accum_alpha_rec = behind * inv;
-            if (!LITE) {
-                for (int ch = 0; ch < 3; ch++) s.accum_normal_rec[ch] = sufN[ch] * inv;
-                s.accum_depth_rec = sufD * inv;
-            }
+            // (the running "behind" value: the upstream gradients dotted with the later samples' weighted sums, over T_end)
+            s.u = bwd_dot<MODE>(s, sufC, behind, sufD, sufN) * inv;
             // (distortion chain: sum over the samples behind of w (D2 + m^2 A - 2 m D); all moments about the tile's
             // reference depth, so the three terms are of the size of their sum)
             if (FULL)
@@ -1764,6 +1763,10 @@ void blend_bwd_kernel(int W, int H, int grid_x, int grid_y, const Header* hdr,
     static_assert(ACC_FLOATS * 4 == SLOT_BYTES && sizeof(float4) * 5 == SLOT_BYTES, "record and accumulator row share the slot offset");
     for (int hi = n_used; hi > seg_begin; hi -= BWD_BATCH) {
         const int cnt = hi - seg_begin < BWD_BATCH ? hi - seg_begin : BWD_BATCH;
+        // (the thread index, opaque to the compiler per batch: the staging and flush addresses are then recomputed from it
+        // each batch instead of kept as induction variables across the walk, which spilled two of them at 80 VGPRs)
+        int tid = (int)threadIdx.x;
+        asm volatile("" : "+v"(tid));
         // slot j of the batch <-> list entry hi - 1 - j.  This pixel's entries are those below its last contributor: slots
         // j > hi - 1 - last_contributor; its median sample is entry median_contributor - 1: slot hi - median_contributor (no
         // median: slot hi, which is not in the batch -- and whose offset no contributing lane holds: the idle slot BWD_BATCH
@@ -1777,18 +1780,18 @@ void blend_bwd_kernel(int W, int H, int grid_x, int grid_y, const Header* hdr,
         {
             // threads 0..127 stage (back to front: slot t <-> list entry hi-1-t) and test their entry against all eight
             // blocks; all threads zero the accumulators
-            const bool have = (int)threadIdx.x < cnt;
+            const bool have = tid < cnt;
             if (wave < BWD_BATCH / 64) {
                 FootprintTest foot = no_footprint();
                 if (have) {
-                    const uint32_t id = point_list[r0 + (uint32_t)(hi - 1 - (int)threadIdx.x)];
-                    s_id[threadIdx.x] = id;
-                    foot = stage_record(s_rec, threadIdx.x, rec, id);
+                    const uint32_t id = point_list[r0 + (uint32_t)(hi - 1 - tid)];
+                    s_id[tid] = id;
+                    foot = stage_record(s_rec, tid, rec, id);
                 }
                 publish_block_masks<BWD_BATCH / 64, 8>(s_mask8, have, foot, tc.tx * TILE, tc.ty * TILE, wave, 0, lane,
                                                        flags & FLAG_NO_CULL);
             }
-            for (int i = threadIdx.x; i < BWD_BATCH * ACC_FLOATS / 4; i += 256)
+            for (int i = tid; i < BWD_BATCH * ACC_FLOATS / 4; i += 256)
                 reinterpret_cast<float4*>(s_acc)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
         __syncthreads();
@@ -1868,7 +1871,7 @@ void blend_bwd_kernel(int W, int H, int grid_x, int grid_y, const Header* hdr,
         __syncthreads();
         // flush: consecutive lanes take consecutive floats of a record, so that the atomics of one wave instruction
         // fall into ~6 cache lines (3.2 records of 80 B) instead of 64
-        for (int idx = threadIdx.x; idx < cnt * ACC_FLOATS; idx += 256) {
+        for (int idx = tid; idx < cnt * ACC_FLOATS; idx += 256) {
             const float val = s_acc[idx];
 #if SURFEL_ABLATE & 4   // (... and the global flush)
             if (val == 123.456f) {

@@ -742,23 +742,39 @@ SURFEL_HD bool fwd_accumulate(FwdPixel& s, const PairEval& e, const float normal
     return true;
 }
 
-// Backward per-pixel state (backward.cu:192-244).  The reference carries last_alpha / last_color /
-// last_depth / last_normal and folds the previous sample into the accum_*_rec running values at the
-// START of the next processed sample (backward.cu:337, :371, :375, :380).  Here the same update
-// (same operands, same operations, hence the same bits) is applied at the END of the sample that
-// produced them, which removes eight carried registers and their copies from the inner loop.
+// Backward per-pixel state (backward.cu:192-244).  The reference carries eight running "what lies behind" values per pixel
+// (accum_rec[3], accum_depth_rec, accum_alpha_rec, accum_normal_rec[3]: x <- alpha f + (1 - alpha) x over the features f
+// = rgb, depth, 1, normal of the samples processed so far, backward.cu:337-380), and uses each of them only in
+// dL/dalpha += (f - x) g, with g the pixel's upstream gradient of that plane -- a per-pixel constant.  The recurrence is
+// linear, so the dot product u = sum g x obeys the same one, u <- u + alpha (phi - u) with phi = sum g f (bwd_dot), and the
+// eight terms of dL/dalpha are phi - u: one carried register instead of eight, a dot product of the entry's features
+// instead of three instructions per plane.  (The same differences, summed in another order: fp32 rounds differently.)
 struct BwdPixel {
     float T, T_final;
     float dL_dpixel[3];
     float dL_ddepth, dL_daccum, dL_dreg, dL_dnormal2D[3], dL_dmedian_depth, dL_dmax_dweight;
     float final_D, final_D2, final_A;
     float bg_dot_dpixel;
-    float accum_rec[3] = {0, 0, 0};
-    float accum_depth_rec = 0, accum_alpha_rec = 0, accum_normal_rec[3] = {0, 0, 0};
+    float u = 0;  // sum over the planes of (upstream gradient) x (what lies behind), see above
     float last_dL_dT = 0;
     uint32_t last_contributor, median_contributor;
     float m0 = 0;  // the tile's reference mapped depth (FwdPixel): final_D, final_D2 are moments of m - m0
 };
+
+// The pixel's upstream gradients dotted with the features (colour c, alpha-plane value a, depth d, normal n): colour first,
+// then the alpha plane, then depth and normal, so that the LITE sum is the full one before the terms that are exact
+// zeros there (x + 0 d == x).
+template <int MODE = BLEND_FULL>
+SURFEL_HD float bwd_dot(const BwdPixel& s, const float c[3], float a, float d, const float n[3])
+{
+    float r = fmaf(c[2], s.dL_dpixel[2], fmaf(c[1], s.dL_dpixel[1], c[0] * s.dL_dpixel[0]));
+    r = fmaf(a, s.dL_daccum, r);
+    if (MODE != BLEND_LITE) {
+        r = fmaf(d, s.dL_ddepth, r);
+        for (int ch = 0; ch < 3; ch++) r = fmaf(n[ch], s.dL_dnormal2D[ch], r);
+    }
+    return r;
+}
 
 // The part of one (pixel, surfel) pair's backward that runs through the pixel's back-to-front recurrences
 // (backward.cu:325-400): advances the pixel state and returns the blend weight w = alpha * T, dL/dalpha
@@ -780,14 +796,13 @@ SURFEL_HD PairGrad bwd_pair_core(BwdPixel& s, const PairEval& e, const float nor
     const float inv_1ma = fast_rcp(one_m_alpha);
     s.T = s.T * inv_1ma;
     const float w = alpha * s.T;
-    float dL_dalpha = 0.0f;
-    for (int ch = 0; ch < 3; ch++) dL_dalpha += (rgb[ch] - s.accum_rec[ch]) * s.dL_dpixel[ch];
+    // the eight "behind" terms of dL/dalpha at once, and the pixel's running value advanced past this sample
+    const float lin = bwd_dot<MODE>(s, rgb, 1.0f, c_d, normal) - s.u;
+    s.u = fmaf(alpha, lin, s.u);
+    float dL_dalpha = lin;
     if (MODE == BLEND_LITE) {
-        dL_dalpha += (1.0f - s.accum_alpha_rec) * s.dL_daccum;
         dL_dalpha *= s.T;
         dL_dalpha += (-s.T_final * inv_1ma) * s.bg_dot_dpixel;
-        for (int ch = 0; ch < 3; ch++) s.accum_rec[ch] = fmaf(alpha, rgb[ch] - s.accum_rec[ch], s.accum_rec[ch]);
-        s.accum_alpha_rec = fmaf(alpha, 1.0f - s.accum_alpha_rec, s.accum_alpha_rec);
         PairGrad r;
         r.w = w;
         r.dL_dalpha = dL_dalpha;
@@ -812,22 +827,8 @@ SURFEL_HD PairGrad bwd_pair_core(BwdPixel& s, const PairEval& e, const float nor
         dL_dz += dL_dmd * dmd_dd;
     }
 
-    dL_dalpha += (c_d - s.accum_depth_rec) * s.dL_ddepth;
-    dL_dalpha += (1.0f - s.accum_alpha_rec) * s.dL_daccum;
-    for (int ch = 0; ch < 3; ch++) dL_dalpha += (normal[ch] - s.accum_normal_rec[ch]) * s.dL_dnormal2D[ch];
     dL_dalpha *= s.T;
     dL_dalpha += (-s.T_final * inv_1ma) * s.bg_dot_dpixel;
-
-    // fold this sample into the running "what lies behind" values (see the struct comment)
-    // x <- x + alpha (c - x): the differences are the ones dL_dalpha was just built from, so each running value costs one
-    // FMA instead of a multiplication and an FMA (8 of the ~210 VALU instructions of a pair evaluation: blend_bwd -2.4 %).
-    // backward.cu:337-380 writes alpha c + (1 - alpha) x; the two round differently by an ulp of x.
-    for (int ch = 0; ch < 3; ch++) {
-        s.accum_rec[ch] = fmaf(alpha, rgb[ch] - s.accum_rec[ch], s.accum_rec[ch]);
-        s.accum_normal_rec[ch] = fmaf(alpha, normal[ch] - s.accum_normal_rec[ch], s.accum_normal_rec[ch]);
-    }
-    s.accum_depth_rec = fmaf(alpha, c_d - s.accum_depth_rec, s.accum_depth_rec);
-    s.accum_alpha_rec = fmaf(alpha, 1.0f - s.accum_alpha_rec, s.accum_alpha_rec);
     dL_dz += w * s.dL_ddepth;
     PairGrad r;
     r.w = w;
